@@ -2,6 +2,15 @@
 """bench.py -- device-resident 128-bit Meow key-hash throughput on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c4g|c64|...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up the keys, settles and warms up, times the K steps, writes
+the last step's outputs if --dump-outputs is given, and prints the JSON line
+(value, ms_per_step, and the roofline figures the timed steps' own HIP events
+give).  Everything that takes runs of its own -- the parity of the timed
+output against the reference, the poisoned relaunch, the 1-GPU c4g scaling
+anchor, the copy-peak probe, the PCIe-inclusive host pipeline and the CPU
+baseline -- runs only with --full.
 
 A "step" is one pass of the hot path (one kvh_meow128_* launch) over one
 batch of synthetic keys already resident in HBM.  Default workload at every
@@ -12,13 +21,13 @@ independent: there is no data-path collective; a CPU gloo group only carries
 the barrier and the max-over-ranks time.  BASELINE configs[4] as stated (c4g:
 ONE global batch of 1B 32-byte keys, rank r hashing index range
 shard_range(1B, r, N), "scaling": "strong") runs with --config c4g and reads
-against its 1-GPU anchor, which the default N=1 line carries.
+against its 1-GPU anchor, which the default N=1 line carries under --full.
 
 The JSON line carries
   roofline     : algorithmic bytes/launch / avg kernel time (HIP events on
                  the launch stream) against 8 TB/s HBM; `traffic` from the
                  committed rocprofv3 PMC summary for this workload, if any;
-  cpu_baseline : the reference CPU path (oracle/_ref: the unmodified
+  cpu_baseline : (--full) the reference CPU path (oracle/_ref: the unmodified
                  src/key_hash.c kv_hash_meow128) on this box's host cores,
                  rank 0 at N=1 only, bounded sample; falls back to the
                  clean-room oracle port if the reference build is absent.
@@ -513,7 +522,7 @@ def resolve_config(name, rank: int, world: int, keys_override: int = 0):
     return name, cfg, n_global
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs = ranks; without WORLD_SIZE in the environment bench.py starts them itself")
@@ -523,6 +532,14 @@ def main():
                     help="default: c1 per GPU at every N (weak scaling); c4g = BASELINE configs[4] as stated "
                          "(one global 1B x 32 B batch, strong scaling)")
     ap.add_argument("--keys", type=int, default=0, help="override keys per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: parity of the timed output against the "
+                         "reference and the poisoned relaunch, the 1-GPU c4g scaling anchor, the copy-peak probe, "
+                         "the PCIe-inclusive host pipeline and the CPU baseline (each has its own --no-... switch); "
+                         "without --full the run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float64 words; "
+                         "a fixed seeded sample of a large output, see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--e2e", dest="e2e", action="store_true", default=None,
@@ -536,7 +553,11 @@ def main():
                     help="skip the 1-GPU c4g scaling anchor (measured after c1 at N=1 and by every rank at N>1)")
     ap.add_argument("--parity-keys", type=int, default=20_000,
                     help="keys of the timed launch's output checked against the reference after the timed region")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     # N ranks: under torch.distributed.run WORLD_SIZE is set and must agree
     # with --gpus; without it bench.py starts the N ranks itself (fresh child
@@ -688,8 +709,12 @@ def main():
     T = {k: v for k, v in locals().items() if k in ("keys", "offs_np", "out", "hashes", "pos", "crc_out", "s_h", "s_ho",
                                                      "s_io", "sorter", "geom", "text", "t_offs", "t_lens", "t_out",
                                                      "t_cnt")}
+    dumped = None
+    if args.dump_outputs:  # before any later leg launches into these buffers again
+        dumped = dump_outputs(args.dump_outputs, timed_outputs(cfg, T, out), f".rank{rank}" if world > 1 else "")
     try:
-        par = timed_parity(args.config, cfg, seed, T, args.parity_keys, rank) if args.parity_keys > 0 else None
+        par = (timed_parity(args.config, cfg, seed, T, args.parity_keys, rank)
+               if args.full and args.parity_keys > 0 else None)
     except Exception as e:  # reported, never hidden: a failed check is not a pass
         par = {"checked": 0, "mismatches": None, "error": repr(e)[:300]}
     # every output word of the path, on the device: the timed output equals a
@@ -705,7 +730,8 @@ def main():
     per_rank = kdist.gather({"rank": rank, "kernel_ms": kern_ms, "keys": n, "parity": par}, world)
     # the scaling anchor: the c4g workload on ONE GPU (N = 1: after the c1 line; N > 1: each rank in turn)
     anchors = None
-    if not args.no_anchor and ((world == 1 and args.config == "c1") or (world > 1 and cfg.get("global_batch"))):
+    if args.full and not args.no_anchor and ((world == 1 and args.config == "c1") or
+                                             (world > 1 and cfg.get("global_batch"))):
         a = None
         for r in range(world):
             kdist.barrier(world)
@@ -754,7 +780,11 @@ def main():
         "hashes_per_s_per_gpu": n * arity / (kern_ms * 1e-3),
         "hashes_per_s_aggregate": n_hash / wall,
         "lds_roofline": lds_line(args.config, units, kern_ms),
+        "full": args.full,
     }
+    if dumped is not None:
+        res["outputs_dumped"] = {"dir": args.dump_outputs, "format": "float64, one 32-bit word per element",
+                                 "arrays": dumped}
     if par is not None:
         pr = [p["parity"] for p in per_rank]
         res["parity"] = {"checked": sum(p.get("checked") or 0 for p in pr),
@@ -775,15 +805,15 @@ def main():
             res.update(anchor_efficiency(world, value, res["per_gpu"], anchors))
     res["roofline"]["guide_copy_peak"] = GUIDE_COPY_GBS
     res["roofline"]["frac_vs_guide_copy"] = achieved / GUIDE_COPY_GBS
-    if rank == 0 and world == 1 and not args.no_copy_peak:
+    if args.full and rank == 0 and world == 1 and not args.no_copy_peak:
         cp = copy_peak(alg_bytes)
         if cp.get("copy_GBps"):
             res["roofline"]["achievable_peak"] = cp["copy_GBps"]
             res["roofline"]["frac_vs_achievable"] = achieved / cp["copy_GBps"]
         res["roofline"]["achievable_source"] = cp
-    if args.e2e and rank == 0 and world == 1:
+    if args.full and args.e2e and rank == 0 and world == 1:
         res["e2e_pcie"] = e2e(kvh, cfg, seed)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             if cfg.get("positions"):
                 res["cpu_baseline"] = cpu_baseline_positions(cfg, seed, args.cpu_seconds, geom)
@@ -884,6 +914,57 @@ def timed_parity(name, cfg, seed, T, k: int, rank: int) -> dict:
     return r
 
 
+def timed_outputs(cfg, T, out) -> dict:
+    """The device tensors a caller of the timed path receives, by name (the
+    ingest outputs cut to the token count the device wrote)."""
+    if cfg.get("ingest"):
+        k = int(T["t_cnt"].item())
+        return {"token_offsets": T["t_offs"][:k], "token_lengths": T["t_lens"][:k], "hashes": T["t_out"][:k]}
+    if cfg.get("sort"):
+        return {"sorted_hashes": T["s_ho"], "sorted_items": T["s_io"]}
+    if cfg.get("crc"):
+        return {"crc": T["crc_out"]}
+    if cfg.get("positions"):
+        return {"positions": T["pos"], **({"hashes": T["hashes"]} if cfg["positions"] == "fused" else {})}
+    return {"hashes": out}
+
+
+DUMP_BYTES = 60_000_000  # all files of one --dump-outputs together (the limit is 64 MB)
+
+
+def dump_outputs(dirname, outs: dict, suffix: str = "") -> dict:
+    """--dump-outputs: what the last timed step left in each output, written
+    as DIR/<name>.npy.  The outputs are integer words (u64 hashes, positions
+    and items, u32 CRCs), so each row is stored as its little-endian 32-bit
+    words in float64, which holds them exactly.  An output too large for its
+    share of DUMP_BYTES is sampled at fixed seeded rows plus the first and
+    the last (DIR/<name>_rows.npy holds the row numbers), and
+    DIR/<name>_fold.npy carries the wrapping 64-bit sum of every (signed)
+    32-bit word column of the WHOLE output, in 16-bit pieces, so two builds
+    can be compared over all of it."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in outs.items():
+        rows = t.shape[0]
+        wpr = t.element_size() * int(np.prod(t.shape[1:], dtype=np.int64)) // 4  # 32-bit words per row
+        w = t.contiguous().view(torch.int32).reshape(rows, wpr)
+        cap = DUMP_BYTES // len(outs) // (8 * (wpr + 1))
+        if rows > cap:
+            idx = np.unique(np.concatenate([[0, rows - 1],
+                                            np.random.default_rng(20240531).integers(0, rows, cap - 2)]))
+            sample = w[torch.from_numpy(idx).to(w.device)]
+        else:
+            idx, sample = np.arange(rows, dtype=np.int64), w
+        fold = torch.sum(w, 0, dtype=torch.int64).cpu().numpy().view(np.uint64)
+        pieces = np.stack([(fold >> np.uint64(s)) & np.uint64(0xffff) for s in (0, 16, 32, 48)], axis=1)
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), sample.cpu().numpy().view(np.uint32).astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}_rows{suffix}.npy"), idx.astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}_fold{suffix}.npy"), pieces.astype(np.float64))
+        written[name] = {"rows": int(rows), "rows_written": int(len(idx)), "words32_per_row": int(w.shape[1])}
+    return written
+
+
 POISON = 0xA5
 
 
@@ -895,17 +976,7 @@ def full_compare(kvh, cfg, T, run, out) -> dict:
     order (knob 24 = 1).  Every key's output must be rewritten, identically,
     by both orders (src/key_hash.c:1413-1429: every key has a hash)."""
     import torch
-    if cfg.get("ingest"):
-        k = int(T["t_cnt"].item())
-        outs = [T["t_offs"][:k], T["t_lens"][:k], T["t_out"][:k]]
-    elif cfg.get("sort"):
-        outs = [T["s_ho"], T["s_io"]]
-    elif cfg.get("crc"):
-        outs = [T["crc_out"]]
-    elif cfg.get("positions"):
-        outs = [T["pos"]] + ([T["hashes"]] if cfg["positions"] == "fused" else [])
-    else:
-        outs = [out]
+    outs = list(timed_outputs(cfg, T, out).values())
     timed = [t.clone() for t in outs]
     word = int.from_bytes(bytes([POISON]) * 8, "little", signed=True)
     res = {"words": int(sum(t.numel() for t in outs)), "against": "the timed output, whole, on the device"}

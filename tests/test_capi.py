@@ -90,10 +90,10 @@ def test_product_library_exports_only_the_header():
         assert prev == dflt and lib.kvh_set_tuning(knob, prev) == val, (knob, val)
 
 
-def test_cpp_host_mirror_compiles():
+def test_cpp_host_mirror_compiles(tmp_path):
     # the C++ KeyFragment/HashSeed mirror is header-only over the C-ABI
     src = '#include "raikv_amd/key_hash.hpp"\nint main(){ kvh::KeyBuf kb("hello"); return kb.keylen == 6 ? 0 : 1; }\n'
-    exe = "/tmp/kvh_mirror_check"
+    exe = str(tmp_path / "kvh_mirror_check")
     r = subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-x", "c++", "-", "-o", exe,
                         "-L", os.path.join(ROOT, "raikv_amd"), "-lkvh", "-Wl,-rpath," + os.path.join(ROOT, "raikv_amd")],
                        input=src, text=True, capture_output=True)

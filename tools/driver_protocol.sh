@@ -7,7 +7,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/drv}; CFG=${2:-c1}
 export TMPDIR=/tmp
 mkdir -p $OUT
-B="python3 bench.py --gpus 1 --config $CFG --no-cpu-baseline"
+B="python3 bench.py --full --gpus 1 --config $CFG --no-cpu-baseline"
 timeout -k 10 150 $B --steps 20 --warmup 5 > $OUT/plain_w5_k20_a.json 2> $OUT/plain_a.log &&
 timeout -k 10 150 $B --steps 100 --warmup 100 > $OUT/plain_w100_k100.json 2> $OUT/plain_b.log &&
 timeout -k 10 150 $B --steps 20 --warmup 5 > $OUT/plain_w5_k20_b.json 2> $OUT/plain_c.log &&

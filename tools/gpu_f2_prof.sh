@@ -2,7 +2,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=${1:-gpurun_out/f2prof}; mkdir -p $O
-B="python3 bench.py --config f2 --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-copy-peak --settle-ms 0"
+B="python3 bench.py --full --config f2 --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-copy-peak --settle-ms 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $B > $O/bench.json 2> $O/trace.err || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- $B > $O/fetch.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- $B > $O/write.log 2>&1 || exit 1

@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 mkdir -p $OUT
 for c in $CFGS; do
   mkdir -p $OUT/$c
-  B="python3 bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-copy-peak"
+  B="python3 bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-copy-peak"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$c/trace -o run -- $B > $OUT/$c/bench.json 2> $OUT/$c/trace.err || exit 1
-  R="python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-e2e --no-copy-peak --settle-ms 0"
+  R="python3 bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline --no-e2e --no-copy-peak --settle-ms 0"
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$c/fetch -o run -- $R > $OUT/$c/fetch.log 2>&1 || exit 1
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/$c/write -o run -- $R > $OUT/$c/write.log 2>&1 || exit 1
   python3 tools/pmc_summary.py $OUT/$c/fetch $OUT/$c/write > $OUT/$c/pmc_summary.json || exit 1
