@@ -309,6 +309,73 @@ int kvh_meow128_fixed_positions(const void *keys, uint32_t key_len, size_t n,
                                 void *pos, uint32_t flags, void *stream);
 
 /* ---------------------------------------------------------------------
+ * Batched find on a table image: what KeyCtx::find answers for a key
+ * (src/key_ctx.cpp:203-216, include/raikv/ht_search.h:308-367), for n keys in
+ * one launch, read-only, over a device-resident COPY of ht[0 .. ht_size)
+ * (HashTab::get_entry(0): KV_HT_HDR_SIZE + KV_HT_CTX_SIZE + KV_HT_STATS_SIZE
+ * = 448 KiB into the map; hash_entry_size x ht_size bytes) that nothing
+ * writes while the call runs.  Entry fields read (hash_entry.h:240-247,
+ * :175-180, :355): hash u64 at +0, hash2 u64 at +8, flags u16 at +20
+ * (FL_DROPPED 0x800), the seal = bit 15 of the u32 at hash_entry_size - 8.
+ * hash_entry_size: a multiple of 32, at least 32.  The geometry is validated
+ * as by kvh_ht_positions; hashes are (h1,h2) pairs already fixed up.
+ *
+ * The walk is find<Position>'s over the slots kvh_ht_positions computes:
+ * from ht_mod(h1), an entry whose hash == h1 with its seal set and hash2 ==
+ * h2 ends it (KeyCtx::equals compares hash2 only, key_ctx.h:245-246):
+ * KVH_KEY_OK, or KVH_KEY_NOT_FOUND when FL_DROPPED; hash == 0 ends it
+ * KVH_KEY_NOT_FOUND at that slot; otherwise the next slot of the ring, and
+ * on a cuckoo table after cuckoo_buckets slots the next of cuckoo_arity
+ * windows at CuckooAltHash::pos[inc] (ht_cuckoo.h:135-141,
+ * ht_cuckoo.cpp:488-507), KVH_KEY_NOT_FOUND after the last; a linear table
+ * (cuckoo_buckets <= 1, key_ctx.cpp:209-215) ends KVH_KEY_HT_FULL after
+ * ht_size slots (ht_linear.cpp:33-41).  ONE DIVERGENCE: where the reference
+ * spins -- an entry with hash == h1 whose seal is clear, or a hash with
+ * ZOMBIE64 (bit 63) set -- a snapshot cannot change, so that key is reported
+ * KVH_KEY_BUSY (retry it through kv_find); the walk never loops: at most
+ * arity x buckets probes, or ht_size on a linear table.
+ *
+ * res[i] = status | inc << 8 | min(chains, 0xFFFF) << 16, with KeyCtx's inc
+ * (the number of the last window searched; arity - 1 when the windows ran
+ * out) and chains (slots passed over).  pos[i] (u64, or u32 with KVH_POS32)
+ * is the slot the walk ended at, or ~0 when it ended without one (windows
+ * exhausted, KVH_KEY_HT_FULL, KVH_KEY_BUSY: the reference leaves kctx.pos
+ * unset there).  entries_out (may be NULL; else n x hash_entry_size bytes,
+ * 16-byte aligned) row i: the matched entry for KVH_KEY_OK -- what find
+ * copies into its work entry (ht_search.h:290-306), immediate value
+ * included -- and zeros for every other status.  n == 0 returns 0 without a
+ * launch.  Asynchronous on stream; nothing is allocated in the call.
+ * ------------------------------------------------------------------- */
+/* KeyStatus values of include/raikv/key_ctx.h as res[] carries them */
+#define KVH_KEY_OK         0
+#define KVH_KEY_NOT_FOUND  2
+#define KVH_KEY_BUSY       3
+#define KVH_KEY_HT_FULL    5
+
+/* Replaces, per key, kctx.set_hash(h1, h2); kctx.find(&wrk) and the read of
+ * kctx.pos / kctx.inc / kctx.chains / kctx.entry.  entries, hashes 16-byte
+ * aligned device pointers. */
+int kvh_ht_find(const void *entries, uint32_t hash_entry_size,
+                const kvh_ht_geom_t *geom, const uint64_t *hashes, size_t n,
+                void *pos, uint32_t *res, void *entries_out,
+                uint32_t flags, void *stream);
+
+/* Fused: n fixed-length keys -> kv_hash_meow128 with (seed1, seed2) ->
+ * KeyFragment fixup -> the find above (KeyCtx::set_key_hash then find,
+ * key_ctx.cpp:97-105, :203-216).  `hashes` (2n u64) receives the fixed-up
+ * hashes.  One kernel for key_len 16/32 with 16-byte aligned keys and
+ * 1/2/4/8 positions per key (the shapes kvh_meow128_fixed_positions fuses),
+ * where hashes may be NULL; other shapes run the hash kernel into `hashes`
+ * and then the find kernel on the same stream, and need it (KVH_EINVAL for
+ * NULL: the call allocates nothing). */
+int kvh_meow128_fixed_find(const void *keys, uint32_t key_len, size_t n,
+                           uint64_t seed1, uint64_t seed2,
+                           const void *entries, uint32_t hash_entry_size,
+                           const kvh_ht_geom_t *geom, uint64_t *hashes /*may be NULL*/,
+                           void *pos, uint32_t *res, void *entries_out,
+                           uint32_t flags, void *stream);
+
+/* ---------------------------------------------------------------------
  * Batch order by table position: the role of
  * kv_ht_radix_sort (src/radix_sort.cpp:31-41) + ctest.c:96-104's duplicate
  * marking.  CONTRACT: the slot sequence equals kv_ht_radix_sort's (ht_mod(h1)

@@ -166,6 +166,24 @@ inline void hash_fixed_positions(const void* keys, uint32_t key_len, size_t n, c
   check(kvh_meow128_fixed_positions(keys, key_len, n, hs.hash1, hs.hash2, &g, hashes, pos, 0u, stream),
         "kvh::hash_fixed_positions");
 }
+// Batched KeyCtx::find on a quiescent device copy of ht[] (entries: ht_size x hash_entry_size bytes):
+// pos[i] = the slot or ~0, res[i] = status | inc << 8 | min(chains, 0xFFFF) << 16 (KVH_KEY_*), and with
+// entries_out (n x hash_entry_size bytes, may be null) the matched entry of a KVH_KEY_OK key, else zeros.
+inline uint32_t find_status(uint32_t res) { return res & 0xFFu; }
+inline uint32_t find_inc(uint32_t res) { return (res >> 8) & 0xFFu; }
+inline uint32_t find_chains(uint32_t res) { return res >> 16; }
+inline void ht_find(const void* entries, uint32_t hash_entry_size, const kvh_ht_geom_t& g, const uint64_t* hashes,
+                    size_t n, uint64_t* pos, uint32_t* res, void* entries_out = nullptr, void* stream = nullptr) {
+  check(kvh_ht_find(entries, hash_entry_size, &g, hashes, n, pos, res, entries_out, 0u, stream), "kvh::ht_find");
+}
+// fused: fixed-length keys -> fixed-up hash pairs (hashes, may be null for 16/32-byte keys) -> find.
+inline void hash_fixed_find(const void* keys, uint32_t key_len, size_t n, const HashSeed& hs, const void* entries,
+                            uint32_t hash_entry_size, const kvh_ht_geom_t& g, uint64_t* hashes, uint64_t* pos,
+                            uint32_t* res, void* entries_out = nullptr, void* stream = nullptr) {
+  check(kvh_meow128_fixed_find(keys, key_len, n, hs.hash1, hs.hash2, entries, hash_entry_size, &g, hashes, pos, res,
+                               entries_out, 0u, stream),
+        "kvh::hash_fixed_find");
+}
 
 // Device scratch owned by the caller-side helpers below (grown on demand,
 // reused across calls; not thread-safe, one per stream).

@@ -29,6 +29,12 @@ from .binding import (  # noqa: F401
     kv_crc_c,
     ht_positions,
     meow128_fixed_positions,
+    ht_find,
+    meow128_fixed_find,
+    KVH_KEY_OK,
+    KVH_KEY_NOT_FOUND,
+    KVH_KEY_BUSY,
+    KVH_KEY_HT_FULL,
     KvhError,
     lib,
     lib_path,
@@ -54,4 +60,5 @@ __all__ = [
     "kv_hash_meow64", "HashSeed", "KeyFragment", "STATIC_SEED", "KVH_POS32", "HtGeom", "ht_positions",
     "meow128_fixed_positions", "crc_c_fixed", "crc_c_var", "kv_crc_c",
     "tokenize", "tokenize_hash", "frag_offsets", "frags_hash", "meow128_spans", "meow128_frags", "KVH_NULTERM", "HtSorter", "ht_sort_batched", "ht_sort_segments", "KVH_DEDUP", "KVH_REF_ORDER", "set_poison_outputs",
+    "ht_find", "meow128_fixed_find", "KVH_KEY_OK", "KVH_KEY_NOT_FOUND", "KVH_KEY_BUSY", "KVH_KEY_HT_FULL",
 ]

@@ -25,6 +25,8 @@ KVH_NULTERM = 0x4
 KVH_DEDUP = 0x8
 KVH_REF_ORDER = 0x10
 KVH_MAX_ARITY = 8
+# KeyStatus values in the low byte of ht_find's res (include/raikv/key_ctx.h)
+KVH_KEY_OK, KVH_KEY_NOT_FOUND, KVH_KEY_BUSY, KVH_KEY_HT_FULL = 0, 2, 3, 5
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KVH_LIB: research tools (tools/*.py) point this at the experiments build
@@ -112,6 +114,8 @@ def _load():
         "kvh_positions_per_key": (U32, [P]),
         "kvh_ht_positions": (I, [P, SZ, P, P, U32, P]),
         "kvh_meow128_fixed_positions": (I, [P, U32, SZ, U64, U64, P, P, P, U32, P]),
+        "kvh_ht_find": (I, [P, U32, P, P, SZ, P, P, P, U32, P]),
+        "kvh_meow128_fixed_find": (I, [P, U32, SZ, U64, U64, P, U32, P, P, P, P, P, U32, P]),
         "kvh_crc_c_fixed": (I, [P, U32, SZ, P, U32, P, P]),
         "kvh_crc_c_var": (I, [P, P, SZ, P, U32, P, P]),
         "kvh_crc_c": (U32, [P, SZ, U32]),
@@ -295,6 +299,59 @@ def meow128_fixed_positions(keys, key_len: int, seed: Tuple[int, int], geom: "Ht
                                           _dev_ptr(out) if n else None, KVH_POS32 if pos32 else 0,
                                           _stream_ptr(stream)), "kvh_meow128_fixed_positions")
     return hashes, out
+
+
+def _entries_ptr(entries, geom: "HtGeom", entry_size: int) -> int:
+    if entries.numel() * entries.element_size() != int(geom.ht_size) * entry_size:
+        raise KvhError(f"entries: expected ht_size x entry_size = {int(geom.ht_size)} x {entry_size} bytes, "
+                       f"got {entries.numel() * entries.element_size()}")
+    return _dev_ptr(entries)
+
+
+def ht_find(entries, geom: "HtGeom", hashes, entry_size: int = 64, pos32: bool = False, gather: bool = False,
+            stream=None):
+    """Batched read-only KeyCtx::find (ht_search.h:308-367) over a device
+    copy of ht[] (`entries`: a contiguous device tensor of ht_size x
+    entry_size bytes that nothing writes meanwhile).  hashes: int64 device
+    tensor [n, 2] of fixed-up (h1, h2).  Returns (pos, res, rows):
+    pos [n] int64 (int32 bit patterns with pos32), the slot or ~0; res [n]
+    int32 = status | inc << 8 | min(chains, 0xFFFF) << 16 (KVH_KEY_OK /
+    KVH_KEY_NOT_FOUND / KVH_KEY_BUSY / KVH_KEY_HT_FULL); rows [n, entry_size]
+    uint8 with gather (the matched entry of a KVH_KEY_OK key, else zeros),
+    None without."""
+    n = hashes.numel() // 2
+    dev = hashes.device
+    pos = _empty((n,), torch.int32 if pos32 else torch.int64, dev)
+    res = _empty((n,), torch.int32, dev)
+    rows = _empty((n, entry_size), torch.uint8, dev) if gather else None
+    check(lib.kvh_ht_find(_entries_ptr(entries, geom, entry_size), entry_size, C.byref(geom),
+                          _dev_ptr(hashes) if n else None, n, _dev_ptr(pos) if n else None,
+                          _dev_ptr(res) if n else None, _dev_ptr(rows) if (gather and n) else None,
+                          KVH_POS32 if pos32 else 0, _stream_ptr(stream, pos, res, rows, hashes, entries)), "kvh_ht_find")
+    return pos, res, rows
+
+
+def meow128_fixed_find(keys, key_len: int, seed: Tuple[int, int], entries, geom: "HtGeom", entry_size: int = 64,
+                       keep_hashes: bool = True, pos32: bool = False, gather: bool = False, stream=None):
+    """Fused fixed-length hash -> fixup -> ht_find (one kernel for 16/32-byte
+    keys, else the hash kernel then the find kernel).  Returns (hashes [n, 2]
+    or None, pos, res, rows) as ht_find."""
+    n = keys.numel() // key_len if key_len else 0
+    dev = keys.device
+    fused = key_len in (16, 32) and geom.per_key in (1, 2, 4, 8) and keys.data_ptr() % 16 == 0
+    hashes = _new_out((n, 2), keys) if (keep_hashes or not fused) else None  # the two-kernel path needs them
+    pos = _empty((n,), torch.int32 if pos32 else torch.int64, dev)
+    res = _empty((n,), torch.int32, dev)
+    rows = _empty((n, entry_size), torch.uint8, dev) if gather else None
+    check(lib.kvh_meow128_fixed_find(_dev_ptr(keys) if n else None, key_len, n, U64(seed[0] & (2**64 - 1)),
+                                     U64(seed[1] & (2**64 - 1)), _entries_ptr(entries, geom, entry_size),
+                                     entry_size, C.byref(geom),
+                                     _dev_ptr(hashes) if (hashes is not None and n) else None,
+                                     _dev_ptr(pos) if n else None, _dev_ptr(res) if n else None,
+                                     _dev_ptr(rows) if (gather and n) else None, KVH_POS32 if pos32 else 0,
+                                     _stream_ptr(stream, hashes, pos, res, rows, keys, entries)),
+          "kvh_meow128_fixed_find")
+    return (hashes if keep_hashes else None), pos, res, rows
 
 
 class HtSorter:

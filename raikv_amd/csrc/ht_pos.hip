@@ -313,6 +313,15 @@ bool fused_ok(uint32_t key_len, uint32_t a, const void* keys) {
 
 }  // namespace
 
+// the same checks and geometry for the find kernels (ht_find.hip)
+namespace kvh {
+namespace rt {
+int ht_check_geom(const kvh_ht_geom_t* g, bool p32) { return check_geom(g, p32); }
+uint32_t ht_per_key(const kvh_ht_geom_t* g) { return per_key(g); }
+HtGeom ht_dev_geom(const kvh_ht_geom_t* g) { return dev_geom(g); }
+}  // namespace rt
+}  // namespace kvh
+
 extern "C" {
 
 int kvh_ht_geom_init(uint64_t map_size, uint32_t hash_entry_size, float hash_value_ratio,

@@ -13,6 +13,8 @@ namespace kvh {
 
 constexpr int kBlock = 1024;  // threads per workgroup of the streaming kernels (16 waves)
 
+struct HtGeom;  // ht_pos.hpp
+
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 
@@ -306,6 +308,11 @@ int launch_done();
 int stream_tickets(hipStream_t st, unsigned long long** tk);
 // kvh_stream_release: synchronise `st` and hand its ticket words back
 int stream_release(hipStream_t st);
+// table geometry (ht_pos.hip; HtGeom: ht_pos.hpp), shared with ht_find.hip: kvh_ht_positions' validation
+// (0 or KVH_EINVAL), positions per key, and the kernel-argument form
+int ht_check_geom(const kvh_ht_geom_t* g, bool p32);
+uint32_t ht_per_key(const kvh_ht_geom_t* g);
+HtGeom ht_dev_geom(const kvh_ht_geom_t* g);
 // kv_ht_radix_sort's exact order on the device, n <= 64K (ht_refsort.hip)
 size_t refsort_segments_scratch_bytes(size_t nseg, uint32_t max_seg);
 int refsort_segments_launch(const uint64_t* hashes, const uint64_t* items, size_t n, const uint64_t* seg_offs,
