@@ -376,6 +376,91 @@ int kvh_meow128_fixed_find(const void *keys, uint32_t key_len, size_t n,
                            uint32_t flags, void *stream);
 
 /* ---------------------------------------------------------------------
+ * Batched get on a table image: the find above followed by what
+ * KeyCtx::value (src/key_ctx.cpp:959-1001) answers, for n keys in one launch,
+ * read-only, over device-resident COPIES of ht[0 .. ht_size) (as for
+ * kvh_ht_find) and of the data segments: map bytes [seg_start, seg_start +
+ * nsegs x seg_size) (FileHdr::seg_start / seg_size / nsegs, shm_ht.h:149-179;
+ * kvh_seg_geom_init), 16-byte aligned, that nothing writes while the call
+ * runs.  `segments` may be NULL when nsegs == 0.  hash_entry_size: a multiple
+ * of 32, at least 64.
+ *
+ * After a find that ends KVH_KEY_OK at an entry, value() switches on flags &
+ * (FL_SEGMENT_VALUE 0x40 | FL_IMMEDIATE_VALUE 0x100) (hash_entry.h:122-124):
+ *   immediate  size = ValueCtr::size, the low 15 bits of the u32 at
+ *              hash_entry_size - 8 (hash_entry.h:175-180); data at entry
+ *              offset 24 with FL_PART_KEY (0x400), else 24 + align8(keylen),
+ *              keylen the u16 at +22 (HashEntry::hdr_size2, immediate_value,
+ *              hash_entry.h:276-281, :308-310).
+ *   segment    the ValuePtr (u16 segment, u16 serialhi, u32 seriallo, u32
+ *              size, u32 offset; hash_entry.h:143-164) at hash_entry_size -
+ *              24, 8 lower with FL_EXPIRE_STAMP | FL_UPDATE_STAMP (0x3000)
+ *              and 8 lower with FL_SEQNO (0x10) (HashEntry::value_ptr,
+ *              hash_entry.h:333-340); size and offset << seg_align_shift.
+ *              HashTab::seg_data (shm_ht.h:468-474): segment >= nsegs or
+ *              offset >= seg_size -> KVH_KEY_MUTATED; else the message
+ *              (msg_ctx.h:16-62) at segment x seg_size + offset.
+ *              MsgHdr::check_seal (msg_ctx.h:113-132; attach_msg(ATTACH_READ)
+ *              + is_msg_valid, key_ctx.cpp:481-524, :565-571) must hold, else
+ *              KVH_KEY_MUTATED: msg.size (u32 +0) == size, msg.hash (+8) ==
+ *              h1, msg.hash2 (+16) == h2, msg.flags (u16 +30) without FL_BUSY
+ *              (0x8000), the trailer ValueCtr at size - 8 with the pointer's
+ *              serial and its seal set, msg.seriallo (u32 +24) == seriallo.
+ *              size = msg.msg_size (u32 +4); data at message offset
+ *              align8(34 + keylen), keylen the u16 at +32 (MsgHdr::hdr_size,
+ *              msg_ctx.h:65-75).
+ *   neither bit, or both: KVH_KEY_NO_VALUE.
+ * A find status other than KVH_KEY_OK is the key's status and it has no
+ * value.  ONE MORE DIVERGENCE, beside KVH_KEY_BUSY: the reference checks no
+ * bounds (it trusts a live table); this call never reads outside the two
+ * images and reports KVH_KEY_MUTATED (retry the key through kv_find /
+ * kv_value) for a ValuePtr with size < 48 or offset + size > seg_size, a
+ * message whose header + msg_size + 8 exceeds msg.size, and an immediate
+ * value whose offset + size exceeds hash_entry_size - 8.  A table the
+ * reference wrote holds none of these.
+ *
+ * pos, res: as kvh_ht_find packs them (KVH_POS32 honoured), the status being
+ * the combined one; for KVH_KEY_MUTATED / KVH_KEY_NO_VALUE pos, inc and chains
+ * stay what find reports.  val_len[i]: the full value size, 0 unless
+ * KVH_KEY_OK.  val_loc[i] (val_loc may be NULL): where value()'s pointer
+ * points, as an offset -- bit 63 set: into the segment image, clear: into
+ * the entry image; the low bits: the byte offset from that image's start;
+ * ~0 unless KVH_KEY_OK.  values_out (may be NULL; else n x val_stride bytes,
+ * 16-byte aligned, val_stride a non-zero multiple of 16) row i: the first
+ * min(val_len, val_stride) value bytes, then zeros; all zeros unless
+ * KVH_KEY_OK.  A longer value is truncated: the caller sees it from val_len
+ * and asks again with a larger stride.  n == 0 returns 0 without a launch.
+ * Asynchronous on stream; nothing is allocated in the call.  There is no
+ * fused-from-keys form: chain kvh_meow128_fixed(..., KVH_FIXUP) and
+ * kvh_ht_get on one stream.
+ * ------------------------------------------------------------------- */
+#define KVH_KEY_MUTATED    6
+#define KVH_KEY_NO_VALUE   8
+
+typedef struct {
+  uint64_t seg_size;        /* FileHdr::seg_size()       shm_ht.h:174-176 */
+  uint32_t nsegs;           /* FileHdr::nsegs            shm_ht.h:152 */
+  uint32_t seg_align_shift; /* FileHdr::seg_align_shift  shm_ht.h:154 */
+} kvh_seg_geom_t;
+
+/* HashTab::initialize's segment geometry (src/ht_init.cpp:118-192) for a map
+ * of map_size bytes: nsegs, seg_size, seg_align_shift and (seg_start may be
+ * NULL) the map offset of segment 0; nsegs = 0 for max_value_size == 0.
+ * Host only. */
+int kvh_seg_geom_init(uint64_t map_size, uint32_t hash_entry_size,
+                      float hash_value_ratio, uint32_t max_value_size,
+                      kvh_seg_geom_t *out, uint64_t *seg_start);
+
+/* Replaces, per key, kctx.set_hash(h1, h2); kctx.find(&wrk);
+ * kctx.value(&ptr, size) and the copy of the value.  entries, segments,
+ * hashes, values_out 16-byte aligned device pointers. */
+int kvh_ht_get(const void *entries, uint32_t hash_entry_size, const kvh_ht_geom_t *geom,
+               const void *segments, const kvh_seg_geom_t *sgeom,
+               const uint64_t *hashes, size_t n,
+               void *pos, uint32_t *res, uint64_t *val_loc, uint32_t *val_len,
+               void *values_out, uint32_t val_stride, uint32_t flags, void *stream);
+
+/* ---------------------------------------------------------------------
  * Batch order by table position: the role of
  * kv_ht_radix_sort (src/radix_sort.cpp:31-41) + ctest.c:96-104's duplicate
  * marking.  CONTRACT: the slot sequence equals kv_ht_radix_sort's (ht_mod(h1)

@@ -184,6 +184,20 @@ inline void hash_fixed_find(const void* keys, uint32_t key_len, size_t n, const 
                                entries_out, 0u, stream),
         "kvh::hash_fixed_find");
 }
+// Batched KeyCtx::find + KeyCtx::value on quiescent device copies of ht[] and of the data segments (segments:
+// sg.nsegs x sg.seg_size bytes, null when nsegs == 0): pos, res as ht_find (status also KVH_KEY_MUTATED /
+// KVH_KEY_NO_VALUE), val_len[i] = the value size, val_loc[i] (may be null) = its offset (get_loc_*), and with
+// values_out (n x val_stride bytes, may be null) the first min(val_len, val_stride) value bytes, then zeros.
+inline bool get_loc_in_segments(uint64_t loc) { return (loc >> 63) != 0; }
+inline uint64_t get_loc_offset(uint64_t loc) { return loc & ~(1ull << 63); }
+inline void ht_get(const void* entries, uint32_t hash_entry_size, const kvh_ht_geom_t& g, const void* segments,
+                   const kvh_seg_geom_t& sg, const uint64_t* hashes, size_t n, uint64_t* pos, uint32_t* res,
+                   uint64_t* val_loc, uint32_t* val_len, void* values_out = nullptr, uint32_t val_stride = 0,
+                   void* stream = nullptr) {
+  check(kvh_ht_get(entries, hash_entry_size, &g, segments, &sg, hashes, n, pos, res, val_loc, val_len, values_out,
+                   val_stride, 0u, stream),
+        "kvh::ht_get");
+}
 
 // Device scratch owned by the caller-side helpers below (grown on demand,
 // reused across calls; not thread-safe, one per stream).

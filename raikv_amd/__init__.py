@@ -31,6 +31,10 @@ from .binding import (  # noqa: F401
     meow128_fixed_positions,
     ht_find,
     meow128_fixed_find,
+    SegGeom,
+    ht_get,
+    KVH_KEY_MUTATED,
+    KVH_KEY_NO_VALUE,
     KVH_KEY_OK,
     KVH_KEY_NOT_FOUND,
     KVH_KEY_BUSY,
@@ -61,4 +65,5 @@ __all__ = [
     "meow128_fixed_positions", "crc_c_fixed", "crc_c_var", "kv_crc_c",
     "tokenize", "tokenize_hash", "frag_offsets", "frags_hash", "meow128_spans", "meow128_frags", "KVH_NULTERM", "HtSorter", "ht_sort_batched", "ht_sort_segments", "KVH_DEDUP", "KVH_REF_ORDER", "set_poison_outputs",
     "ht_find", "meow128_fixed_find", "KVH_KEY_OK", "KVH_KEY_NOT_FOUND", "KVH_KEY_BUSY", "KVH_KEY_HT_FULL",
+    "SegGeom", "ht_get", "KVH_KEY_MUTATED", "KVH_KEY_NO_VALUE",
 ]

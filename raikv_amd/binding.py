@@ -27,6 +27,8 @@ KVH_REF_ORDER = 0x10
 KVH_MAX_ARITY = 8
 # KeyStatus values in the low byte of ht_find's res (include/raikv/key_ctx.h)
 KVH_KEY_OK, KVH_KEY_NOT_FOUND, KVH_KEY_BUSY, KVH_KEY_HT_FULL = 0, 2, 3, 5
+# and of ht_get's: what KeyCtx::value adds
+KVH_KEY_MUTATED, KVH_KEY_NO_VALUE = 6, 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KVH_LIB: research tools (tools/*.py) point this at the experiments build
@@ -68,6 +70,30 @@ class HtGeom(C.Structure):
     def ht_mod(self, k: int) -> int:
         """FileHdr::ht_mod (shm_ht.h:181-184), host side."""
         return (((k & self.ht_mod_mask) * self.ht_mod_fraction) & (2**64 - 1)) >> self.ht_mod_shift
+
+
+class SegGeom(C.Structure):
+    """kvh_seg_geom_t: the FileHdr fields HashTab::seg_data and the ValuePtr
+    decoding read (include/raikv/shm_ht.h:148-179).  `seg_start` (not part of
+    the C struct) is the map offset of segment 0 when made by from_map."""
+    _fields_ = [("seg_size", C.c_uint64), ("nsegs", C.c_uint32), ("seg_align_shift", C.c_uint32)]
+    seg_start = 0
+
+    @classmethod
+    def from_map(cls, map_size: int, hash_entry_size: int = 64, hash_value_ratio: float = 1.0,
+                 max_value_size: int = 0) -> "SegGeom":
+        """HashTab::initialize's segment geometry (ht_init.cpp:118-192)."""
+        g = cls()
+        start = U64(0)
+        check(lib.kvh_seg_geom_init(map_size, hash_entry_size, hash_value_ratio, max_value_size, C.byref(g),
+                                    C.byref(start)), "kvh_seg_geom_init")
+        g.seg_start = int(start.value)
+        return g
+
+    @property
+    def nbytes(self) -> int:
+        """size of the segment image: nsegs x seg_size"""
+        return int(self.nsegs) * int(self.seg_size)
 
 
 def _load():
@@ -116,6 +142,8 @@ def _load():
         "kvh_meow128_fixed_positions": (I, [P, U32, SZ, U64, U64, P, P, P, U32, P]),
         "kvh_ht_find": (I, [P, U32, P, P, SZ, P, P, P, U32, P]),
         "kvh_meow128_fixed_find": (I, [P, U32, SZ, U64, U64, P, U32, P, P, P, P, P, U32, P]),
+        "kvh_seg_geom_init": (I, [U64, U32, C.c_float, U32, P, P]),
+        "kvh_ht_get": (I, [P, U32, P, P, P, P, SZ, P, P, P, P, P, U32, U32, P]),
         "kvh_crc_c_fixed": (I, [P, U32, SZ, P, U32, P, P]),
         "kvh_crc_c_var": (I, [P, P, SZ, P, U32, P, P]),
         "kvh_crc_c": (U32, [P, SZ, U32]),
@@ -352,6 +380,39 @@ def meow128_fixed_find(keys, key_len: int, seed: Tuple[int, int], entries, geom:
                                      _stream_ptr(stream, hashes, pos, res, rows, keys, entries)),
           "kvh_meow128_fixed_find")
     return (hashes if keep_hashes else None), pos, res, rows
+
+
+def ht_get(entries, geom: "HtGeom", segments, sgeom: "SegGeom", hashes, entry_size: int = 64, stride: int = 64,
+           pos32: bool = False, want_loc: bool = True, copy: bool = True, stream=None):
+    """Batched read-only KeyCtx::find + KeyCtx::value (key_ctx.cpp:959-1001)
+    over device copies of ht[] (`entries`, as ht_find) and of the data
+    segments (`segments`: a contiguous device tensor of sgeom.nsegs x
+    sgeom.seg_size bytes, or None when nsegs == 0) that nothing writes
+    meanwhile.  hashes: int64 device tensor [n, 2] of fixed-up (h1, h2).
+    Returns (pos, res, val_len, val_loc, rows): pos, res as ht_find, the
+    status also KVH_KEY_MUTATED / KVH_KEY_NO_VALUE; val_len [n] int32, the
+    full value size (0 unless KVH_KEY_OK); val_loc [n] int64 with want_loc
+    (bit 63: segment image, low bits: byte offset; ~0 unless KVH_KEY_OK), None
+    without; rows [n, stride] uint8 with copy (the first min(val_len, stride)
+    value bytes, then zeros), None without."""
+    n = hashes.numel() // 2
+    dev = hashes.device
+    if segments is not None and segments.numel() * segments.element_size() != sgeom.nbytes:
+        raise KvhError(f"segments: expected nsegs x seg_size = {int(sgeom.nsegs)} x {int(sgeom.seg_size)} bytes, "
+                       f"got {segments.numel() * segments.element_size()}")
+    pos = _empty((n,), torch.int32 if pos32 else torch.int64, dev)
+    res = _empty((n,), torch.int32, dev)
+    vlen = _empty((n,), torch.int32, dev)
+    vloc = _empty((n,), torch.int64, dev) if want_loc else None
+    rows = _empty((n, stride), torch.uint8, dev) if copy else None
+    check(lib.kvh_ht_get(_entries_ptr(entries, geom, entry_size), entry_size, C.byref(geom),
+                         _dev_ptr(segments) if (segments is not None and segments.numel()) else None, C.byref(sgeom),
+                         _dev_ptr(hashes) if n else None, n, _dev_ptr(pos) if n else None,
+                         _dev_ptr(res) if n else None, _dev_ptr(vloc) if (want_loc and n) else None,
+                         _dev_ptr(vlen) if n else None, _dev_ptr(rows) if (copy and n) else None, stride,
+                         KVH_POS32 if pos32 else 0,
+                         _stream_ptr(stream, pos, res, vlen, vloc, rows, hashes, entries, segments)), "kvh_ht_get")
+    return pos, res, vlen, vloc, rows
 
 
 class HtSorter:
